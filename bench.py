@@ -6,6 +6,14 @@ HBM, one checksum per page, bit-exact with contrib/crc32.  A "step" is one
 pass of the engine over the whole batch (one kernel launch).
 
     python bench.py [--gpus N] [--steps K] [--warmup W] [--workload pages4k|pages8k|zipf|chunks]
+                    [--dump-outputs DIR] [--full]
+
+A plain run sets up the batch, runs W untimed and K timed steps, writes the
+last step's results if --dump-outputs is given (dump_outputs below; the inputs
+are a fixed splitmix64 stream, so two builds can be compared array for array)
+and prints the result line.  --full adds what takes work of its own: the
+parity check of the last result against the reference's digests (`parity_ok`,
+exit status 3 on a mismatch; null in a plain run) and the `cpu_baseline` legs.
 
 N > 1: one rank per GPU.  Started as `python bench.py --gpus N` (no
 WORLD_SIZE in the environment) it launches `torch.distributed.run
@@ -28,7 +36,7 @@ Rank 0 prints ONE JSON line.  `value` is GiB/s of buffer bytes read, whole
 job, from the host clock around the K timed steps.  `roofline.achieved` is the
 dominant kernel's algorithmic bytes per launch (buffer bytes + 4 B checksum
 per buffer [+ per-buffer metadata]) / its average launch duration measured
-with HIP events on the launch stream.  `cpu_baseline` times the reference's
+with HIP events on the launch stream.  `cpu_baseline` (--full) times the reference's
 own crc32c.cpp (oracle/_ref) single-threaded on a bounded sample of the same
 workload on this host.
 """
@@ -59,8 +67,13 @@ def parse():
     p.add_argument("--steps", type=int, default=20)
     p.add_argument("--warmup", type=int, default=5, help="untimed steps (the driver's setting)")
     p.add_argument("--workload", default="pages4k", choices=sorted(W.WORKLOADS))
-    p.add_argument("--cpu-seconds", type=float, default=10.0, help="CPU baseline budget (0 disables)")
-    p.add_argument("--no-verify", action="store_true")
+    p.add_argument("--full", action="store_true",
+                   help="also check the last result against the reference's digests (parity_ok) and time the "
+                        "CPU baselines; a plain run only sets up, warms up, times the steps and prints the line")
+    p.add_argument("--dump-outputs", metavar="DIR", default=None,
+                   help="after the timed steps, write what the last step computed as DIR/<name>.npy")
+    p.add_argument("--cpu-seconds", type=float, default=10.0, help="with --full: CPU baseline budget (0 disables)")
+    p.add_argument("--no-verify", action="store_true", help="with --full: skip the parity check")
     p.add_argument("--dry-cpu", action="store_true",
                    help="test the multi-rank harness on CPU (gloo, host checksums); not a measurement")
     p.add_argument("--force-pg", action="store_true",
@@ -140,6 +153,57 @@ def cpu_baseline_threads(wl, seconds, threads=16):
             "sample": f"{sample.desc}; {n} threads over contiguous slices, best of {reps} passes"}
 
 
+DUMP_CAP = 48 << 20  # bytes of .npy payload per rank, all arrays together
+
+
+def dump_outputs(wl, outdir, rank):
+    """--dump-outputs: the arrays a caller of the timed path receives
+    (wl.outputs()), as the last timed step left them, one DIR/<name>.npy each
+    (rank r > 0: <name>_rank<r>.npy).  Integers up to 32 bits are exact in
+    float32 (8 and 16 bits) or float64 (32 bits); 64-bit values are written as
+    two float64 arrays, <name>_lo and <name>_hi, their low and high 32 bits.
+    An array over its share of DUMP_CAP is cut to a fixed sample of rows
+    (numpy default_rng(0), ascending), listed in <name>_index.npy."""
+    os.makedirs(outdir, exist_ok=True)
+    arrays = wl.outputs()
+    share = DUMP_CAP // len(arrays)
+    tag = f"_rank{rank}" if rank else ""
+
+    def save(name, a):
+        np.save(os.path.join(outdir, f"{name}{tag}.npy"), a)
+
+    for name, a in arrays.items():
+        rows = int(a.shape[0])
+        per_row = 1
+        for d in a.shape[1:]:
+            per_row *= int(d)
+        size = a.element_size() if isinstance(a, torch.Tensor) else a.dtype.itemsize
+        row_bytes = per_row * {1: 4, 2: 4, 4: 8, 8: 16}[size]
+        idx = None
+        if rows * row_bytes > share:
+            idx = np.sort(np.random.default_rng(0).choice(rows, share // (row_bytes + 8), replace=False))
+        if isinstance(a, torch.Tensor):
+            if idx is not None and a.dtype == torch.uint8:  # sample on the device, copy the sample only
+                a, idx_done = a[torch.from_numpy(idx).to(a.device)], True
+            else:
+                idx_done = False
+            a = a.cpu().numpy()
+            if idx is not None and not idx_done:
+                a = a[idx]
+        elif idx is not None:
+            a = a[idx]
+        if idx is not None:
+            save(name + "_index", idx.astype(np.float64))
+        if a.dtype.kind == "f":
+            save(name, a.astype(np.float32 if a.dtype.itemsize < 8 else np.float64))
+        elif a.dtype.itemsize == 8:
+            u = np.ascontiguousarray(a).view(np.uint64)
+            save(name + "_lo", (u & np.uint64(0xFFFFFFFF)).astype(np.float64))
+            save(name + "_hi", (u >> np.uint64(32)).astype(np.float64))
+        else:
+            save(name, a.astype(np.float64 if a.dtype.itemsize == 4 else np.float32))
+
+
 def launch_ranks(args):
     """`--gpus N` without an outer launcher: run torch.distributed.run on this
     script as a child process (never an exec: nothing here has touched the GPU
@@ -158,6 +222,8 @@ def main():
     args = parse()
     if args.gpus < 1:
         sys.exit("bench.py: --gpus must be >= 1")
+    if args.steps < 1 or args.warmup < 0:
+        sys.exit("bench.py: --steps must be >= 1 and --warmup >= 0")
     if args.gpus > 1 and "WORLD_SIZE" not in os.environ:
         sys.exit(launch_ranks(args))
     world = int(os.environ.get("WORLD_SIZE", "1"))
@@ -217,8 +283,11 @@ def main():
     elapsed = time.perf_counter() - t0
     kernel_ms = ev0.elapsed_time(ev1) / args.steps if timed else elapsed / args.steps * 1e3
 
+    if args.dump_outputs:
+        dump_outputs(wl, args.dump_outputs, rank)
+
     ok = True
-    if not args.no_verify:
+    if args.full and not args.no_verify:
         ok = wl.verify()
 
     stats = torch.tensor([elapsed, float(wl.bytes_per_step), 0.0 if ok else 1.0, kernel_ms, float(shard)],
@@ -253,11 +322,12 @@ def main():
             "config": dict(wl.config, parallelism=f"{world} GPU(s), independent shards per rank; RCCL only "
                                                   "for max-time / byte-count reduction"),
             "pct_of_hbm_read_peak": round(100.0 * value * GIB / 1e9 / HBM_PEAK_GBS, 2),
-            "parity_ok": bool(ok),
+            "parity_ok": bool(ok) if args.full else None,  # checked with --full only
             "world_size": dist.get_world_size() if use_pg else 1,
             "collective": (dist.get_backend() if use_pg else None),
             "per_rank": [{"rank": i, "shard": int(r[4]), "bytes_per_step": int(r[1]), "elapsed_s": round(r[0], 6),
-                          "avg_launch_ms": round(r[3], 4), "parity_ok": r[2] == 0.0} for i, r in enumerate(per_rank)],
+                          "avg_launch_ms": round(r[3], 4), "parity_ok": r[2] == 0.0 if args.full else None}
+                         for i, r in enumerate(per_rank)],
             "roofline": {
                 "bound": "pcie" if host_timed else "hbm",
                 "kernel": wl.kernel_name,
@@ -273,7 +343,7 @@ def main():
         }
         if dry:
             rec["data"] = "DRY RUN on CPU (harness test, not a measurement)"
-        elif args.cpu_seconds > 0 and world == 1:  # reported at N=1 only
+        elif args.full and args.cpu_seconds > 0 and world == 1:  # reported at N=1 only
             rec["cpu_baseline"] = cpu_baseline(wl, args.cpu_seconds)
             mt = cpu_baseline_threads(wl, min(args.cpu_seconds, 3.0))
             if mt:

@@ -1,6 +1,7 @@
 """Workloads for bench.py (BASELINE.json configs), each a synthetic input of
 the named shape generated directly in HBM (or pinned host memory), plus the
-CPU-baseline sample and a parity check of the last device result.
+CPU-baseline sample, a parity check of the last device result, and outputs():
+the arrays a caller of the timed path receives (bench.py --dump-outputs).
 
 configs[0]  CPU contrib/crc32 on 65536 x 4 KiB pages        -> cpu_baseline of pages4k
 configs[1]  1 Mi x 4 KiB pages, 1 GPU                        -> "pages4k" (default)
@@ -118,6 +119,9 @@ class Pages:
         F.batch_fixed(self.buf, self.page_bytes, self.page_bytes, self.count, seed=self.seed, out=self.out,
                       stream=stream)
 
+    def outputs(self):
+        return {"checksums": self.out}
+
     def verify(self):
         got = self.out.cpu().numpy()
         d = shard_digest(self.page_bytes, self.count, self.seed, self.state)
@@ -204,6 +208,9 @@ class VarLen:
     def step(self, stream):
         F.batch_varlen(self.buf, self.offsets, self.lengths, seed=self.seed, out=self.out, stream=stream)
 
+    def outputs(self):
+        return {"checksums": self.out}
+
     def verify(self):
         got = self.out.cpu().numpy()
         want = _varlen_digest(self.shape, self.h_lengths, self.seed)
@@ -256,6 +263,9 @@ class HostChunks:
 
     def step(self, stream):
         self.pipe.varlen(self.buf, self.h_offsets, self.h_lengths, seed=self.seed, out=self.out)
+
+    def outputs(self):
+        return {"checksums": self.out}
 
     def verify(self):
         want = _varlen_digest("chunks", self.h_lengths, self.seed)
@@ -346,6 +356,9 @@ class DryCpuPages:
         for i in range(self.count):
             self.out[i] = F.crc32c_append(0, self.buf[4096 * i:4096 * (i + 1)])
 
+    def outputs(self):
+        return {"checksums": self.out}
+
     def verify(self):
         return int(self.out[0]) == F.crc32c_append(0, self.buf[:4096].tobytes())
 
@@ -372,6 +385,9 @@ class Xxh3Pages:
 
     def step(self, stream):
         self.X.batch_fixed(self.buf, 4096, self.length, self.count, seed=self.seed, out=self.out, stream=stream)
+
+    def outputs(self):
+        return {"digests": self.out}
 
     def verify(self):
         with open(os.path.join(ROOT, "tests", "golden", "xxh3_golden.json")) as fh:
@@ -437,6 +453,9 @@ class SqliteVerify:
     def step(self, stream):
         self.PC.sqlite_verify_pages(self.buf, 4096, self.count, first_pgno=1, stream=stream, status=self.status,
                                     bad=self.bad)
+
+    def outputs(self):
+        return {"status": self.status, "bad": self.bad}
 
     def verify(self):
         from oracle import oracle as O
@@ -542,6 +561,9 @@ class DiskQueueVerify:
     def step(self, stream):
         self.PC.diskqueue_check_pages(self.buf, self.count, stream=stream, ok=self.ok, bad=self.bad)
 
+    def outputs(self):
+        return {"ok": self.ok, "bad": self.bad}
+
     def verify(self):
         from oracle import oracle as O
         if not torch.equal(self.ok, self.expect):
@@ -587,6 +609,9 @@ class SqliteSeal:
 
     def step(self, stream):
         self.PC.sqlite_seal_pages(self.buf, 4096, self.count, first_pgno=1, stream=stream)
+
+    def outputs(self):
+        return {"pages": self.buf.view(self.count, 4096)}
 
     def verify(self):
         from oracle import oracle as O
@@ -638,6 +663,9 @@ class DiskQueueSeal:
 
     def step(self, stream):
         self.PC.diskqueue_seal_pages(self.buf, self.count, stream=stream)
+
+    def outputs(self):
+        return {"pages": self.buf.view(self.count, 4096)}
 
     def verify(self):
         from oracle import oracle as O
@@ -714,6 +742,9 @@ class RedwoodVerify:
         self.RW.verify_pages(self.buf, self.PS, self.count, first_page_id=self.FIRST, stream=stream,
                              status=self.status, bad=self.nbad)
 
+    def outputs(self):
+        return {"status": self.status, "bad": self.nbad}
+
     def verify(self):
         from oracle import oracle as O
         if not torch.equal(self.status, self.expect):
@@ -767,6 +798,9 @@ class RedwoodSeal:
     def step(self, stream):
         self.RW.seal_pages(self.buf, self.PS, self.count, first_page_id=self.FIRST, stream=stream, status=self.status)
 
+    def outputs(self):
+        return {"status": self.status, "pages": self.buf.view(self.count, self.PS)}
+
     def verify(self):
         from oracle import oracle as O
         if not bool((self.status == 0).all()):
@@ -813,6 +847,9 @@ class Xxh3Zipf(VarLen):
 
     def step(self, stream):
         self.X.batch_varlen(self.buf, self.offsets, self.lengths, out=self.out, stream=stream)
+
+    def outputs(self):
+        return {"digests": self.out}
 
     def verify(self):
         from oracle import oracle as O
@@ -917,6 +954,9 @@ class Xxh3Chained:
         self.X.batch_chained(self.buf, self.seg_off, self.seg_len, self.starts, total_bytes=self.total,
                              out=self.out, stream=stream)
 
+    def outputs(self):
+        return {"digests": self.out}
+
     def verify(self):
         from oracle import oracle as O
         got = self.out.cpu().numpy().view(np.uint64)
@@ -989,6 +1029,10 @@ class PacketsVerify:
 
     def step(self, stream):
         self.V.verify(self.buf, self.boff, self.blen, stream=stream)
+
+    def outputs(self):
+        r = self.V.results_numpy()
+        return {"status": r["status"], "frames": r["frames"], "consumed": r["consumed"]}
 
     def verify(self):
         r = self.V.results_numpy()

@@ -8,7 +8,8 @@ parameters and the reference's outputs only.
 
 Usage (in the container that has /root/reference):
     make -C oracle && python tests/golden/make_golden_xxh3.py [--varlen]
-(--varlen: only (re)compute the varlen_full section, keeping the rest.)
+(--varlen: only (re)compute the varlen_full section, keeping the rest;
+--random: the same for the random section.)
 """
 import json
 import os
@@ -59,11 +60,31 @@ def varlen_full(g):
     g["varlen_full"] = out
 
 
+def random_cases(rng_seed=11, count=400):
+    """The (offset, length, seed) draws of tests/test_xxh3.py's random test over
+    its default_rng(rng_seed) bytes: one generator, drawn in this order."""
+    rng = np.random.default_rng(rng_seed)
+    data = rng.integers(0, 256, 1 << 18, dtype=np.uint8)
+    for _ in range(count):
+        n = int(rng.integers(0, 5000))
+        off = int(rng.integers(0, 64))
+        seed = int(rng.integers(0, 2 ** 63)) if rng.random() < 0.5 else 0
+        yield data[off:off + n], seed
+
+
+def random_section(g):
+    g["random"] = {"rng_seed": 11, "count": 400,
+                   "xxh3": ["%016x" % O.ref_xxh3_64(d, s) for d, s in random_cases(11, 400)]}
+
+
 def main():
-    if "--varlen" in sys.argv:
+    if "--varlen" in sys.argv or "--random" in sys.argv:
         with open(OUT) as fh:
             g = json.load(fh)
-        varlen_full(g)
+        if "--varlen" in sys.argv:
+            varlen_full(g)
+        if "--random" in sys.argv:
+            random_section(g)
         with open(OUT, "w") as fh:
             json.dump(g, fh, indent=0)
         print("wrote", OUT, os.path.getsize(OUT), "bytes")
@@ -113,6 +134,7 @@ def main():
                    "diskqueue": list(O.ref_hashlittle2(pg[16:], 0x12345678, 0xbeefabcd))})
     g["hashlittle2"] = {"kat": kat, "pages": hl}
     varlen_full(g)
+    random_section(g)
     with open(OUT, "w") as f:
         json.dump(g, f, indent=0)
     print("wrote", OUT, os.path.getsize(OUT), "bytes")

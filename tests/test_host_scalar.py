@@ -3,7 +3,8 @@ both implementations -- SSE4.2 (3 streams x 1 KiB, then 3 x 256 B) and the
 sliced-table fallback the reference takes without the crc32 instruction
 (append_table, :124-172, dispatch :344-356) -- against the reference's own
 outputs, every alignment and the tier boundaries; and the same checks through
-a C++ program that includes the REFERENCE's header and links the library."""
+a C++ program that includes the REFERENCE's header and links the library
+(oracle/Makefile compiles it against that header into oracle/_ref/, unlinked)."""
 import json
 import os
 import subprocess
@@ -13,7 +14,7 @@ import numpy as np
 import pytest
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-REF_HDR = "/root/reference/contrib/crc32/include"
+CONSUMER = os.path.join(ROOT, "oracle", "_ref", "ref_header_consumer.a")
 
 CHECK = r"""
 import sys, json, numpy as np
@@ -64,17 +65,17 @@ def test_forced_software_fallback_matches_reference():
     assert res == {"impl": "sliced", "bad": 0}
 
 
-@pytest.mark.skipif(not os.path.exists(os.path.join(REF_HDR, "crc32", "crc32c.h")),
-                    reason="reference tree absent (the consumer compiles against its header)")
+@pytest.mark.skipif(not os.path.exists(CONSUMER),
+                    reason="oracle/_ref not built (the consumer compiles against the reference's header there)")
 def test_compiled_consumer_of_reference_header(tmp_path, golden):
     """A C++ translation unit written against the REFERENCE's header
-    (contrib/crc32/include/crc32/crc32c.h:36-39), linked against
+    (contrib/crc32/include/crc32/crc32c.h:36-39; tests/consumer, compiled by
+    oracle/Makefile where the reference lies), linked here against
     libfdb_crc32c.so instead of contrib/crc32: the link-time drop-in claim."""
     exe = tmp_path / "consumer"
     lib_dir = os.path.dirname(os.environ.get("FDBCRC_LIB") or os.path.join(ROOT, "foundationdb_amd", "lib", "x"))
     lib_name = os.path.basename(os.environ.get("FDBCRC_LIB", "libfdb_crc32c.so"))[3:-3]
-    cmd = ["g++", "-O1", "-std=c++17", "-I", REF_HDR, os.path.join(ROOT, "tests", "consumer", "ref_header_consumer.cpp"),
-           "-L", lib_dir, f"-l{lib_name}", f"-Wl,-rpath,{lib_dir}", "-o", str(exe)]
+    cmd = ["g++", CONSUMER, "-L", lib_dir, f"-l{lib_name}", f"-Wl,-rpath,{lib_dir}", "-o", str(exe)]
     subprocess.run(cmd, check=True, capture_output=True, text=True)
     lines = [f"{k['seed']} {len(bytes.fromhex(k['hex']))} {k['hex'] or '-'} {k['crc']}" for k in golden["kat"]]
     c = golden["chained"]

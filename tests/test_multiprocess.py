@@ -89,7 +89,7 @@ def test_bench_gpus2_launches_two_ranks():
     launcher): bench.py starts two ranks itself, every rank checks the world
     size, and rank 0's single line aggregates both (barrier, max time over
     ranks, byte sum, per-rank kernel times).  --dry-cpu: gloo + host checksums."""
-    r = _bench(["--gpus", "2", "--steps", "3", "--warmup", "1", "--dry-cpu"])
+    r = _bench(["--gpus", "2", "--steps", "3", "--warmup", "1", "--dry-cpu", "--full"])
     assert r.returncode == 0, r.stderr[-3000:]
     lines = [l for l in r.stdout.splitlines() if l.startswith("{")]
     assert len(lines) == 1, r.stdout
@@ -107,7 +107,7 @@ def test_bench_under_outer_launcher():
     port = _free_port()
     cmd = [sys.executable, "-m", "torch.distributed.run", "--nnodes=1", "--nproc-per-node=2",
            "--master-addr=127.0.0.1", f"--master-port={port}", os.path.join(ROOT, "bench.py"),
-           "--gpus", "2", "--steps", "3", "--warmup", "1", "--dry-cpu"]
+           "--gpus", "2", "--steps", "3", "--warmup", "1", "--dry-cpu", "--full"]
     r = subprocess.run(cmd, capture_output=True, text=True, timeout=300, cwd=ROOT,
                        env=dict(os.environ, OMP_NUM_THREADS="1"))
     assert r.returncode == 0, r.stderr[-3000:]
@@ -148,7 +148,7 @@ def test_bench_rccl_path_on_one_gpu():
     cmd = [sys.executable, "-m", "torch.distributed.run", "--nnodes=1", "--nproc-per-node=1",
            "--master-addr=127.0.0.1", f"--master-port={port}", os.path.join(ROOT, "bench.py"),
            "--gpus", "1", "--workload", "pages8k", "--steps", "3", "--warmup", "1", "--force-pg",
-           "--shard-base", "5", "--cpu-seconds", "0"]
+           "--shard-base", "5", "--full", "--cpu-seconds", "0"]
     r = subprocess.run(cmd, capture_output=True, text=True, timeout=240, cwd=ROOT,
                        env=dict(os.environ, MASTER_ADDR="127.0.0.1"))
     assert r.returncode == 0, r.stderr[-3000:]
@@ -158,3 +158,51 @@ def test_bench_rccl_path_on_one_gpu():
     assert rec["world_size"] == 1 and rec["collective"] == "nccl", rec
     assert rec["parity_ok"] and rec["per_rank"][0]["shard"] == 5 and rec["per_rank"][0]["parity_ok"]
     assert "shard 5" in rec["data"] and rec["value"] > 0
+
+
+def test_bench_plain_run_dumps_outputs_and_checks_nothing(tmp_path):
+    """A plain run times exactly --steps steps, reports ms_per_step, does no
+    parity check or CPU baseline (those are --full's), and --dump-outputs
+    writes the last step's checksums: float64, exact, and the same bytes from
+    the same arguments (the dry run's pages are default_rng(shard) bytes)."""
+    r = _bench(["--gpus", "1", "--steps", "4", "--warmup", "1", "--dry-cpu", "--dump-outputs", str(tmp_path / "o")],
+               timeout=120)
+    assert r.returncode == 0, r.stderr[-3000:]
+    lines = [l for l in r.stdout.splitlines() if l.startswith("{")]
+    assert len(lines) == 1, r.stdout
+    rec = json.loads(lines[0])
+    assert rec["steps"] == 4 and rec["warmup"] == 1 and rec["parity_ok"] is None and "cpu_baseline" not in rec
+    assert rec["ms_per_step"] > 0
+    # (value is rounded to 0.01 GiB/s, ms_per_step to 0.1 us)
+    assert rec["value"] == pytest.approx(rec["per_rank"][0]["bytes_per_step"] / (rec["ms_per_step"] * 1e-3) / (1 << 30),
+                                         rel=1e-3, abs=0.006)
+    assert sorted(os.listdir(tmp_path / "o")) == ["checksums.npy"]
+    got = np.load(tmp_path / "o" / "checksums.npy")
+    import foundationdb_amd as F
+    buf = np.random.default_rng(0).integers(0, 256, 2048 * 4096, dtype=np.uint8)
+    want = [F.crc32c_append(0, buf[4096 * i:4096 * (i + 1)]) for i in range(2048)]
+    assert got.dtype == np.float64 and got.shape == (2048,)
+    assert np.array_equal(got, np.array(want, dtype=np.float64))
+
+
+def test_bench_rejects_zero_steps():
+    r = _bench(["--gpus", "1", "--steps", "0", "--warmup", "0", "--dry-cpu"], timeout=120)
+    assert r.returncode != 0 and "--steps must be >= 1" in r.stderr
+    assert not [l for l in r.stdout.splitlines() if l.startswith("{")]
+
+
+@pytest.mark.gpu
+def test_bench_dumped_checksums_are_the_reference_digest(tmp_path, golden):
+    """The headline run's dumped output is every checksum of the 1 Mi page
+    batch: its digest is the one the reference produced (tests/golden
+    pages_full, seed 0), though the plain run itself checks nothing."""
+    sys.path.insert(0, ROOT)
+    import bench_shapes as S
+    r = _bench(["--gpus", "1", "--steps", "2", "--warmup", "1", "--dump-outputs", str(tmp_path)], timeout=200)
+    assert r.returncode == 0, r.stderr[-3000:]
+    rec = json.loads([l for l in r.stdout.splitlines() if l.startswith("{")][0])
+    assert rec["steps"] == 2 and rec["parity_ok"] is None and "cpu_baseline" not in rec and rec["ms_per_step"] > 0
+    got = np.load(tmp_path / "checksums.npy")
+    assert got.dtype == np.float64 and got.shape == (1 << 20,)
+    d = [d for d in golden["pages_full"]["digests"] if d["seed"] == 0][0]
+    assert S.digest(got.astype(np.uint32)) == S.pinned(d)

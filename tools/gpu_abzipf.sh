@@ -16,7 +16,7 @@ for spec in ${LIBS:-prod}; do
   lib=""; [ "$name" != "prod" ] && lib=$PWD/foundationdb_amd/lib/libfdb_crc32c_$name.so
   for w in ${WL:-zipf}; do
     d=gpurun_out/ab/$w-$name-$pass
-    env $envs FDBCRC_LIB=$lib timeout -k 10 300 rocprofv3 --kernel-trace --stats --output-format csv -d $d -o k -- python bench.py --workload $w --steps 20 --cpu-seconds 0 > $d.json 2> $d.err || { tail -5 $d.err; exit 1; }
+    env $envs FDBCRC_LIB=$lib timeout -k 10 300 rocprofv3 --kernel-trace --stats --output-format csv -d $d -o k -- python bench.py --workload $w --steps 20 --full --cpu-seconds 0 > $d.json 2> $d.err || { tail -5 $d.err; exit 1; }
     python - $d/k_kernel_stats.csv $d.json "$w $spec #$pass" <<'PY'
 import csv, sys, json
 rows = [r for r in csv.DictReader(open(sys.argv[1])) if "splitmix" not in r["Name"] and "rocclr" not in r["Name"] and int(r["Calls"]) > 2]

@@ -17,9 +17,9 @@ if [ "${STAGE:-1}" = 1 ]; then
 timeout -k 10 500 python -u -m pytest tests -m gpu -q --timeout 120 --timeout-method thread > $R/pytest_gpu.txt 2>&1 || { tail -5 $R/pytest_gpu.txt; exit 1; }
 tail -1 $R/pytest_gpu.txt
 timeout -k 10 200 python -c "import __graft_entry__ as g; g.smoke()" > $R/smoke.txt 2>&1 || exit 1
-timeout -k 10 300 python bench.py > $R/bench_pages4k.json 2> $R/bench_pages4k.err || exit 1
+timeout -k 10 300 python bench.py --full > $R/bench_pages4k.json 2> $R/bench_pages4k.err || exit 1
 for w in pages8k zipf zipf-scattered chunks chunks-host pages4k-host xxh3-pages4k xxh3-zipf xxh3-chunks xxh3-chained sqlite-verify sqlite-verify-host diskqueue-verify sqlite-seal diskqueue-seal packets-verify redwood-verify redwood-seal; do
-  timeout -k 10 300 python bench.py --workload $w --steps 20 --cpu-seconds 5 > $R/bench_$w.json 2> $R/bench_$w.err || { tail -3 $R/bench_$w.err; exit 1; }
+  timeout -k 10 300 python bench.py --workload $w --steps 20 --full --cpu-seconds 5 > $R/bench_$w.json 2> $R/bench_$w.err || { tail -3 $R/bench_$w.err; exit 1; }
 done
 echo benches done
 # the headline's first launches in a fresh process (bench.py runs --warmup 5)
@@ -30,7 +30,7 @@ grep "model name" /proc/cpuinfo | head -1 > $R/host_cpu.txt
 for f in $R/bench_*.json; do echo "$f $(cut -c1-200 $f)"; done
 exit 0
 fi
-timeout -k 10 300 rocprofv3 --kernel-trace --stats --output-format csv -d $R/prof_pages4k -o pages4k -- python bench.py --cpu-seconds 0 > $R/prof_pages4k.log 2>&1 || exit 1
+timeout -k 10 300 rocprofv3 --kernel-trace --stats --output-format csv -d $R/prof_pages4k -o pages4k -- python bench.py --full --cpu-seconds 0 > $R/prof_pages4k.log 2>&1 || exit 1
 for w in pages8k zipf zipf-scattered chunks xxh3-pages4k xxh3-zipf xxh3-chunks xxh3-chained sqlite-verify diskqueue-verify sqlite-seal diskqueue-seal packets-verify redwood-verify redwood-seal; do
   timeout -k 10 300 rocprofv3 --kernel-trace --stats --output-format csv -d $R/prof_$w -o $w -- python bench.py --workload $w --steps 20 --cpu-seconds 0 --no-verify > $R/prof_$w.log 2>&1 || exit 1
 done
