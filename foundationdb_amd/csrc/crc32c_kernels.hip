@@ -28,8 +28,6 @@
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 
-#include <type_traits>
-
 #include "crc32c_common.h"
 
 #ifndef FDBCRC_PU
@@ -83,57 +81,6 @@ __device__ __forceinline__ void unit_crc_b(const uint32_t* lds, int lane, uint32
 	}
 }
 
-// Strided page layout (STRIDED): lane l reads dword k of a page at byte
-// 4l + 256k -- 16 global_load_dword per page, each 256 contiguous bytes -- and
-// runs ONE register chain over its 16 words at a 256-byte stride:
-//     r' = (r ^ w) * x^(8*256)
-// four lookups per word from the stride4 tables, exactly as the contiguous
-// chain's x^32 step, and no permlane swizzle.  The chain ends at 4l + 4096;
-// the lane multiplies by x^(-8*4l) (lane_s) before the wave XOR.
-struct BlockS {
-	uint32_t w[16];
-};
-typedef __attribute__((address_space(1))) const uint32_t g_u32k;
-__device__ __forceinline__ void load_block_s(BlockS& b, const uint8_t* page, uint32_t lane4) {
-	const uint8_t* p = page + lane4;
-#pragma unroll
-	for (int k = 0; k < 16; ++k) b.w[k] = __builtin_nontemporal_load((g_u32k*)reinterpret_cast<uintptr_t>(p + 256 * k));
-}
-template <int U, bool WINDOW, bool RAW = WINDOW>
-__device__ __forceinline__ void unit_crc_s(const uint32_t* lds, int lane, uint32_t c4, uint32_t c_lane,
-                                           BlockS (&u)[U], const uint32_t (&s)[U], uint32_t (&crc)[U],
-                                           uint32_t h, uint32_t t) {
-	uint32_t x[U];
-	if (WINDOW) {
-		// word 0 of lane l holds bytes [4l, 4l + 4): keep those >= h and XOR in
-		// ~seed at byte h (it reaches lane h/4 and, past a word boundary, the
-		// next lane); word 15 holds [3840 + 4l, +4): keep those < 4096 - t
-		const int d = (int)h - 4 * lane;  // ~seed's byte offset inside the word
-		const uint32_t keep0 = d <= 0 ? ~0u : (d >= 4 ? 0u : ~0u << (8 * d));
-		const int cut = 256 - (int)t - 4 * lane;
-		const uint32_t keep15 = cut >= 4 ? ~0u : (cut <= 0 ? 0u : ~0u >> (8 * (4 - cut)));
-#pragma unroll
-		for (int j = 0; j < U; ++j) {
-			const uint32_t sd = ~s[j];
-			const uint32_t inj = (d > -4 && d < 4) ? (d >= 0 ? sd << (8 * d) : sd >> (-8 * d)) : 0u;
-			x[j] = (u[j].w[0] & keep0) ^ inj;
-			u[j].w[15] &= keep15;
-		}
-	} else {
-#pragma unroll
-		for (int j = 0; j < U; ++j) x[j] = (lane == 0 ? ~s[j] : 0u) ^ u[j].w[0];
-	}
-#pragma unroll
-	for (int w = 0; w < 16; ++w)
-#pragma unroll
-		for (int j = 0; j < U; ++j) x[j] = word_step4_next(lds, x[j], w < 15 ? u[j].w[w + 1] : 0u, c4);
-#pragma unroll
-	for (int j = 0; j < U; ++j) {
-		const uint32_t r = wave_xor(mul_nibbles(lds, x[j], c_lane));
-		crc[j] = RAW ? r : ~r;
-	}
-}
-
 // Lane-parallel multiply of a per-lane value by a constant whose nibble tables
 // live in global memory (8 gathers, L2-resident).
 __device__ __forceinline__ uint32_t vmul_tab(const uint32_t (*tab)[16], uint32_t v) {
@@ -179,10 +126,7 @@ __device__ uint64_t g_bt2[16384][4];  // prep-free start-up: after the scan's ba
 #else
 #define FDBCRC_BT2(k)
 #endif
-#ifndef FDBCRC_STRIDED
-#define FDBCRC_STRIDED 0
-#endif
-template <int U, bool WINDOW = false, bool LIST = false, bool PAIR = false, bool STRIDED = FDBCRC_STRIDED>
+template <int U, bool WINDOW = false, bool LIST = false, bool PAIR = false>
 __global__ __launch_bounds__(1024) void k_pages4k(const uint8_t* __restrict__ base, uint64_t stride, uint64_t count,
                                                   uint32_t seed, const uint32_t* __restrict__ seeds,
                                                   uint32_t* __restrict__ out, const DevTables* __restrict__ tabs,
@@ -220,22 +164,12 @@ __global__ __launch_bounds__(1024) void k_pages4k(const uint8_t* __restrict__ ba
 		if (PAIR) return base + (j >> 1) * stride + (j & 1) * 4096;
 		return base + (LIST ? (uint64_t)idx[j] : j) * stride;
 	};
-	typedef typename std::conditional<STRIDED, BlockS, Block>::type Blk;
-	const uint32_t lane4 = 4u * (uint32_t)c.lane;
-	auto load_u = [&](Blk (&u)[U], uint64_t i0) {
+	auto load_u = [&](Block (&u)[U], uint64_t i0) {
 #pragma unroll
-		for (int j = 0; j < U; ++j) {
-			if constexpr (STRIDED)
-				load_block_s(u[j], page(i0 + j), lane4);
-			else
-				load_block(u[j], page(i0 + j), c.ld_off);
-		}
+		for (int j = 0; j < U; ++j) load_block(u[j], page(i0 + j), c.ld_off);
 	};
-	auto unit = [&](Blk (&u)[U], const uint32_t (&sd)[U], uint32_t (&crc)[U]) {
-		if constexpr (STRIDED)
-			unit_crc_s<U, WINDOW, WINDOW || PAIR>(lds, c.lane, c4, c_lane, u, sd, crc, h, t);
-		else
-			unit_crc_b<U, WINDOW, WINDOW || PAIR>(lds, c.lane, c4, c_lane, u, sd, crc, h, t);
+	auto unit = [&](Block (&u)[U], const uint32_t (&sd)[U], uint32_t (&crc)[U]) {
+		unit_crc_b<U, WINDOW, WINDOW || PAIR>(lds, c.lane, c4, c_lane, u, sd, crc, h, t);
 	};
 	auto clampg = [&](uint64_t g) { return g < g1 ? g : ngrab; };  // ngrab: nothing left
 	auto request = [&]() -> uint32_t {
@@ -260,12 +194,9 @@ __global__ __launch_bounds__(1024) void k_pages4k(const uint8_t* __restrict__ ba
 	// apart at the end: 1 Mi pages 672 -> 667 us, same box, 6 launches each.)
 	uint64_t gA = clampg(g0 + wi), gB = ngrab;
 	uint32_t sdA = seed_of(gA), sdB = 0;
-	Blk u0[U], u1[U];
+	Block u0[U], u1[U];
 	load_u(u0, gA * C);  // in flight during the LDS fill
-	if constexpr (STRIDED)
-		fill_lds_src(lds, &tabs->stride4[0][0], &tabs->lane_s[0][0][0]);
-	else
-		fill_lds_b(lds, tabs);
+	fill_lds_b(lds, tabs);
 	uint32_t mine = 0;     // lane 2U*f + j: checksum of page j of the group's f-th grab
 	uint64_t myi = ~0ull;  // ... and its index in the batch (~0: none)
 	uint32_t f = 0;        // grabs in the current store group
@@ -532,9 +463,8 @@ __device__ NPStart np_start(const BigParams& P, uint32_t* lds, uint32_t ngrid) {
 	}
 	__syncthreads();
 	FDBCRC_BT2(1)
-	// the 16 wave sums, lane-parallel: lanes 0..15 of every wave read them
-	// once and scan them (serial reads took 0.8 us)
-	constexpr uint32_t nw = 16;  // (1024-thread workgroups: blockDim read from memory costs a round trip here)
+	// the 16 wave sums (1024-thread workgroups), lane-parallel: lanes 0..15 of
+	// every wave read them once and scan them (serial reads took 0.8 us)
 	const uint32_t kl = lane & 15;
 	uint64_t sb16 = sB[kl];
 	uint32_t sn16 = sN[kl];

@@ -34,6 +34,7 @@
 
 #include "redwood.h"
 #include "xxh3_device.h"
+#include "xxh3_math.h"
 
 namespace fdbrw {
 
@@ -41,40 +42,21 @@ namespace {
 
 typedef uint32_t u32x4 __attribute__((ext_vector_type(4)));
 
-// The default secret as little-endian u64 words (xxhash.h:2500-2511, algorithm constant).
-__constant__ uint64_t kRSec[24] = {
-    0xbe4ba423396cfeb8ull, 0x1cad21f72c81017cull, 0xdb979083e96dd4deull, 0x1f67b3b7a4a44072ull,
-    0x78e5c0cc4ee679cbull, 0x2172ffcc7dd05a82ull, 0x8e2443f7744608b8ull, 0x4c263a81e69035e0ull,
-    0xcb00c391bb52283cull, 0xa32e531b8b65d088ull, 0x4ef90da297486471ull, 0xd8acdea946ef1938ull,
-    0x3f349ce33f76faa8ull, 0x1d4f0bc7c7bbdcf9ull, 0x3159b4cd4be0518aull, 0x647378d9c97e9fc8ull,
-    0xc3ebd33483acc5eaull, 0xeb6313faffa081c5ull, 0x49daf0b751dd0d17ull, 0x9e68d429265516d3ull,
-    0xfca1477d58be162bull, 0xce31d07ad1b8f88full, 0x280416958f3acb45ull, 0x7e404bbbcafbd7afull,
-};
-constexpr uint64_t P32_1 = 0x9E3779B1u, P32_2 = 0x85EBCA77u, P32_3 = 0xC2B2AE3Du;
-constexpr uint64_t P64_1 = 0x9E3779B185EBCA87ull, P64_2 = 0xC2B2AE3D27D4EB4Full, P64_3 = 0x165667B19E3779F9ull;
-constexpr uint64_t P64_4 = 0x85EBCA77C2B2AE63ull, P64_5 = 0x27D4EB2F165667C5ull;
-
-__device__ __forceinline__ uint64_t mulfold(uint64_t a, uint64_t b) { return a * b ^ __umul64hi(a, b); }
-__device__ __forceinline__ uint64_t rotl64(uint64_t x, int r) { return (x << r) | (x >> (64 - r)); }
-__device__ __forceinline__ uint64_t avalanche3(uint64_t h) {  // xxhash.h:2680-2685
-	h ^= h >> 37;
-	h *= 0x165667919E3779F9ull;
-	return h ^ (h >> 32);
-}
-__device__ __forceinline__ uint64_t avalanche64(uint64_t h) {  // xxhash.h:1711-1718
-	h ^= h >> 33;
-	h *= P64_2;
-	h ^= h >> 29;
-	h *= P64_3;
-	return h ^ (h >> 32);
-}
-// Secret bytes at any offset (default secret): two words and a shift.
-__device__ __forceinline__ uint64_t sec64(uint32_t off) {
-	const uint32_t w = off >> 3, s = (off & 7) * 8;
-	const uint64_t lo = kRSec[w];
-	return s ? (lo >> s) | (kRSec[w + 1] << (64 - s)) : lo;
-}
-__device__ __forceinline__ uint32_t sec32(uint32_t off) { return (uint32_t)sec64(off); }
+using fdbxxh::kSec;
+using fdbxxh::ksec;
+using fdbxxh::ksec32;
+using fdbxxh::mulfold;
+using fdbxxh::P32_1;
+using fdbxxh::P32_2;
+using fdbxxh::P32_3;
+using fdbxxh::P64_1;
+using fdbxxh::P64_2;
+using fdbxxh::P64_3;
+using fdbxxh::P64_4;
+using fdbxxh::P64_5;
+using fdbxxh::rotl64;
+using fdbxxh::xxh3_aval;
+using fdbxxh::xxh64_aval;
 
 // ---- the common layout: a 51-byte header in the page's first 64 bytes ----
 // Bytes [O, O+8) of the 64 bytes held as 16 dwords (O a compile-time offset).
@@ -91,7 +73,7 @@ __device__ __forceinline__ uint64_t rd64c(const uint32_t (&w)[16]) {
 }
 template <int O, int S>
 __device__ __forceinline__ uint64_t mix16c(const uint32_t (&w)[16]) {  // xxhash.h:2834-2863, seed 0
-	return mulfold(rd64c<O>(w) ^ kRSec[S / 8], rd64c<O + 8>(w) ^ kRSec[S / 8 + 1]);
+	return mulfold(rd64c<O>(w) ^ kSec[S / 8], rd64c<O + 8>(w) ^ kSec[S / 8 + 1]);
 }
 // XXH3_64bits of bytes [0, 51) (len_17to128, xxhash.h:2866-2894).
 __device__ __forceinline__ uint64_t xxh3_51(const uint32_t (&w)[16]) {
@@ -100,7 +82,7 @@ __device__ __forceinline__ uint64_t xxh3_51(const uint32_t (&w)[16]) {
 	acc += mix16c<51 - 32, 48>(w);
 	acc += mix16c<0, 0>(w);
 	acc += mix16c<51 - 16, 16>(w);
-	return avalanche3(acc);
+	return xxh3_aval(acc);
 }
 
 // ---- any layout: a byte image of [0, len <= 263) ----------------------------
@@ -123,7 +105,7 @@ struct Img {
 	}
 };
 __device__ uint64_t mix16g(const Img& m, uint32_t k, uint32_t s) {
-	return mulfold(m.rd64(k) ^ sec64(s), m.rd64(k + 8) ^ sec64(s + 8));
+	return mulfold(m.rd64(k) ^ ksec(s), m.rd64(k + 8) ^ ksec(s + 8));
 }
 // XXH3_64bits (seed 0, default secret) of the image's [0, len), len <= 255:
 // the closed forms and, for 241..255 bytes, the long form's single partial
@@ -131,13 +113,13 @@ __device__ uint64_t mix16g(const Img& m, uint32_t k, uint32_t s) {
 __device__ uint64_t xxh3_img(const Img& m, uint32_t len) {
 	if (len <= 16) {
 		if (len > 8) {
-			const uint64_t lo = m.rd64(0) ^ (sec64(24) ^ sec64(32));
-			const uint64_t hi = m.rd64(len - 8) ^ (sec64(40) ^ sec64(48));
-			return avalanche3(len + __builtin_bswap64(lo) + hi + mulfold(lo, hi));
+			const uint64_t lo = m.rd64(0) ^ (ksec(24) ^ ksec(32));
+			const uint64_t hi = m.rd64(len - 8) ^ (ksec(40) ^ ksec(48));
+			return xxh3_aval(len + __builtin_bswap64(lo) + hi + mulfold(lo, hi));
 		}
 		if (len >= 4) {
 			const uint64_t i1 = (uint32_t)m.rd64(0), i2 = (uint32_t)m.rd64(len - 4);
-			uint64_t h = (i2 + (i1 << 32)) ^ (sec64(8) ^ sec64(16));
+			uint64_t h = (i2 + (i1 << 32)) ^ (ksec(8) ^ ksec(16));
 			h ^= rotl64(h, 49) ^ rotl64(h, 24);  // rrmxmx, xxhash.h:2692-2699
 			h *= 0x9FB21C651E98DF25ull;
 			h ^= (h >> 35) + len;
@@ -147,9 +129,9 @@ __device__ uint64_t xxh3_img(const Img& m, uint32_t len) {
 		if (len) {
 			const uint32_t c1 = m.byte(0), c2 = m.byte(len >> 1), c3 = m.byte(len - 1);
 			const uint32_t comb = (c1 << 16) | (c2 << 24) | c3 | (len << 8);
-			return avalanche64((uint64_t)comb ^ (uint64_t)(sec32(0) ^ sec32(4)));
+			return xxh64_aval((uint64_t)comb ^ (uint64_t)(ksec32(0) ^ ksec32(4)));
 		}
-		return avalanche64(sec64(56) ^ sec64(64));
+		return xxh64_aval(ksec(56) ^ ksec(64));
 	}
 	if (len <= 128) {
 		uint64_t acc = len * P64_1;
@@ -167,20 +149,20 @@ __device__ uint64_t xxh3_img(const Img& m, uint32_t len) {
 		}
 		acc += mix16g(m, 0, 0);
 		acc += mix16g(m, len - 16, 16);
-		return avalanche3(acc);
+		return xxh3_aval(acc);
 	}
 	if (len <= 240) {
 		uint64_t acc = len * P64_1;
 		for (uint32_t i = 0; i < 8; ++i) acc += mix16g(m, 16 * i, 16 * i);
-		acc = avalanche3(acc);
+		acc = xxh3_aval(acc);
 		for (uint32_t i = 8; i < len / 16; ++i) acc += mix16g(m, 16 * i, 16 * (i - 8) + 3);
 		acc += mix16g(m, len - 16, 136 - 17);
-		return avalanche3(acc);
+		return xxh3_aval(acc);
 	}
 	uint64_t acc[8] = {P32_3, P64_1, P64_2, P64_3, P64_4, P32_2, P64_5, P32_1};
 	auto stripe = [&](uint32_t k, uint32_t s) {  // accumulate_512, xxhash.h:3474-3488
 		for (uint32_t i = 0; i < 8; ++i) {
-			const uint64_t v = m.rd64(k + 8 * i), x = v ^ sec64(s + 8 * i);
+			const uint64_t v = m.rd64(k + 8 * i), x = v ^ ksec(s + 8 * i);
 			acc[i ^ 1] += v;
 			acc[i] += (uint64_t)(uint32_t)x * (x >> 32);
 		}
@@ -188,8 +170,8 @@ __device__ uint64_t xxh3_img(const Img& m, uint32_t len) {
 	for (uint32_t s = 0; s < (len - 1) / 64; ++s) stripe(64 * s, 8 * s);
 	stripe(len - 64, 192 - 64 - 7);
 	uint64_t r = (uint64_t)len * P64_1;
-	for (uint32_t i = 0; i < 4; ++i) r += mulfold(acc[2 * i] ^ sec64(11 + 16 * i), acc[2 * i + 1] ^ sec64(19 + 16 * i));
-	return avalanche3(r);
+	for (uint32_t i = 0; i < 4; ++i) r += mulfold(acc[2 * i] ^ ksec(11 + 16 * i), acc[2 * i + 1] ^ ksec(19 + 16 * i));
+	return xxh3_aval(r);
 }
 
 __device__ __forceinline__ void load64(const uint8_t* p, uint32_t (&w)[16]) {

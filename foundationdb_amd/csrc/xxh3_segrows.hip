@@ -19,34 +19,16 @@
 #include <stdint.h>
 
 #include "xxh3_device.h"
+#include "xxh3_math.h"
 
 namespace fdbxxh {
 
 namespace {
 
-// The default secret as little-endian u64 words (xxhash.h:2500-2511, algorithm constant).
-__constant__ uint64_t kSegSec[24] = {
-    0xbe4ba423396cfeb8ull, 0x1cad21f72c81017cull, 0xdb979083e96dd4deull, 0x1f67b3b7a4a44072ull,
-    0x78e5c0cc4ee679cbull, 0x2172ffcc7dd05a82ull, 0x8e2443f7744608b8ull, 0x4c263a81e69035e0ull,
-    0xcb00c391bb52283cull, 0xa32e531b8b65d088ull, 0x4ef90da297486471ull, 0xd8acdea946ef1938ull,
-    0x3f349ce33f76faa8ull, 0x1d4f0bc7c7bbdcf9ull, 0x3159b4cd4be0518aull, 0x647378d9c97e9fc8ull,
-    0xc3ebd33483acc5eaull, 0xeb6313faffa081c5ull, 0x49daf0b751dd0d17ull, 0x9e68d429265516d3ull,
-    0xfca1477d58be162bull, 0xce31d07ad1b8f88full, 0x280416958f3acb45ull, 0x7e404bbbcafbd7afull,
-};
-constexpr uint64_t P32_1 = 0x9E3779B1u, P32_2 = 0x85EBCA77u, P32_3 = 0xC2B2AE3Du;
-constexpr uint64_t P64_1 = 0x9E3779B185EBCA87ull, P64_2 = 0xC2B2AE3D27D4EB4Full, P64_3 = 0x165667B19E3779F9ull;
-constexpr uint64_t P64_4 = 0x85EBCA77C2B2AE63ull, P64_5 = 0x27D4EB2F165667C5ull;
-
-__device__ __forceinline__ uint64_t sr_mulfold(uint64_t a, uint64_t b) { return a * b ^ __umul64hi(a, b); }
-__device__ __forceinline__ uint64_t sr_aval(uint64_t h) {  // xxhash.h:2680-2685
-	h ^= h >> 37;
-	h *= 0x165667919E3779F9ull;
-	return h ^ (h >> 32);
-}
 // Word j of the secret for `seed` (the custom secret of XXH3_64bits_withSeed,
 // xxhash.h:3550-3566: +seed on the low word of each 16-byte pair, -seed on the high).
 __device__ __forceinline__ uint64_t sr_word(uint32_t j, uint64_t seed) {
-	return (j & 1) ? kSegSec[j] - seed : kSegSec[j] + seed;
+	return (j & 1) ? kSec[j] - seed : kSec[j] + seed;
 }
 // Secret bytes [off, off + 8) for `seed`, any offset.
 __device__ __forceinline__ uint64_t sr_sec(uint32_t off, uint64_t seed) {
@@ -190,10 +172,10 @@ __global__ __launch_bounds__(256) void k_xxh3_segrows(SegRowsP P) {
 			a1 += sr_rowsum(s1w);
 		}
 		// merge (xxhash.h:3678-3700): L * P64_1 + sum over the pairs of mulfold(acc ^ secret + 11 + 16k)
-		uint64_t m = sr_mulfold(a0 ^ sr_sec(11 + 16 * k, sd), a1 ^ sr_sec(19 + 16 * k, sd));
+		uint64_t m = mulfold(a0 ^ sr_sec(11 + 16 * k, sd), a1 ^ sr_sec(19 + 16 * k, sd));
 		m += __shfl_xor(m, 1, 16);
 		m += __shfl_xor(m, 2, 16);
-		if (r == 0) P.out[c] = sr_aval(L * P64_1 + m);
+		if (r == 0) P.out[c] = xxh3_aval(L * P64_1 + m);
 	}
 }
 

@@ -30,34 +30,11 @@
 #include <stdint.h>
 
 #include "xxh3_device.h"
+#include "xxh3_math.h"
 
 namespace fdbxxh {
 
 namespace {
-
-constexpr uint64_t P32_1 = 0x9E3779B1u, P32_2 = 0x85EBCA77u, P32_3 = 0xC2B2AE3Du;
-constexpr uint64_t P64_1 = 0x9E3779B185EBCA87ull, P64_2 = 0xC2B2AE3D27D4EB4Full, P64_3 = 0x165667B19E3779F9ull;
-constexpr uint64_t P64_4 = 0x85EBCA77C2B2AE63ull, P64_5 = 0x27D4EB2F165667C5ull;
-
-// The default secret as 24 little-endian words (xxhash.h:2500-2511).
-__constant__ uint64_t kSecS[24] = {
-    0xbe4ba423396cfeb8ull, 0x1cad21f72c81017cull, 0xdb979083e96dd4deull, 0x1f67b3b7a4a44072ull,
-    0x78e5c0cc4ee679cbull, 0x2172ffcc7dd05a82ull, 0x8e2443f7744608b8ull, 0x4c263a81e69035e0ull,
-    0xcb00c391bb52283cull, 0xa32e531b8b65d088ull, 0x4ef90da297486471ull, 0xd8acdea946ef1938ull,
-    0x3f349ce33f76faa8ull, 0x1d4f0bc7c7bbdcf9ull, 0x3159b4cd4be0518aull, 0x647378d9c97e9fc8ull,
-    0xc3ebd33483acc5eaull, 0xeb6313faffa081c5ull, 0x49daf0b751dd0d17ull, 0x9e68d429265516d3ull,
-    0xfca1477d58be162bull, 0xce31d07ad1b8f88full, 0x280416958f3acb45ull, 0x7e404bbbcafbd7afull,
-};
-
-// Word j of the secret for `seed` (xxhash.h:3550-3566: +seed / -seed per word).
-__device__ __forceinline__ uint64_t swd(int j, uint64_t seed) {
-	const uint64_t w = kSecS[j];
-	return (j & 1) ? w - seed : w + seed;
-}
-// Secret bytes [8j + r, 8j + r + 8), 0 < r < 8.
-__device__ __forceinline__ uint64_t sat(int j, int r, uint64_t seed) {
-	return (swd(j, seed) >> (8 * r)) | (swd(j + 1, seed) << (64 - 8 * r));
-}
 
 template <int CTRL>
 __device__ __forceinline__ void add_dpp(uint32_t& lo, uint32_t& hi) {
@@ -180,8 +157,8 @@ __global__ __launch_bounds__(1024) void k_xlong(XLong S) {
 				__builtin_amdgcn_fence(__ATOMIC_RELEASE, "workgroup");
 				VS[c].claimed = 0;
 			}
-			const uint64_t ck = swd(16 + (int)j, seed);  // scramble key: secret + 128 + 8j
-			const uint64_t gk = sat(1 + (int)j, 3, seed);  // merge key: secret + 11 + 8j
+			const uint64_t ck = sec_word(16 + (int)j, seed);  // scramble key: secret + 128 + 8j
+			const uint64_t gk = sec_at(1 + (int)j, 3, seed);  // merge key: secret + 11 + 8j
 			const uint32_t cklo = (uint32_t)ck, ckhi = (uint32_t)(ck >> 32);
 			// scrambleAcc (xxhash.h:3702-3718) in 32-bit halves: the high half's
 			// product is off the low half's dependent path
@@ -332,14 +309,14 @@ __global__ __launch_bounds__(1024) void k_xlong(XLong S) {
 		const uint64_t sd = SEEDS ? 0 : S.seed;
 #pragma unroll
 		for (int i = 0; i < 4; ++i) {
-			k0[i] = swd(g + 4 * i + 2 * k, sd);
-			k1[i] = swd(g + 4 * i + 2 * k + 1, sd);
+			k0[i] = sec_word(g + 4 * i + 2 * k, sd);
+			k1[i] = sec_word(g + 4 * i + 2 * k + 1, sd);
 		}
-		l0 = sat(15 + 2 * k, 1, sd);
-		l1 = sat(16 + 2 * k, 1, sd);
-		b15 = kSecS[15 + 2 * k];
-		b16 = kSecS[16 + 2 * k];
-		b17 = kSecS[17 + 2 * k];
+		l0 = sec_at(15 + 2 * k, 1, sd);
+		l1 = sec_at(16 + 2 * k, 1, sd);
+		b15 = kSec[15 + 2 * k];
+		b16 = kSec[16 + 2 * k];
+		b17 = kSec[17 + 2 * k];
 	}
 	uint32_t tag_at = 0, tag_v = 0;  // the last computed step's tag, not yet published
 	auto compute = [&](const PStep& St) __attribute__((always_inline)) {
